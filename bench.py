@@ -18,9 +18,29 @@ applied through the public API exactly as a user would call them
 seed's s/gate, window time and pass count (and at N > 1 its swaps, bytes sent
 per rank, swap device time and the swap share of the window).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--qubits Q] [--seeds 7,11,...] [--eager] [--no-extras]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--qubits Q] [--seeds 7,11,...] [--eager]
+                    [--dump-outputs DIR] [--full [--extras a,b | --no-extras]]
 
-Besides the headline, a single-GPU run adds (outside the timed region, ~10 s):
+A plain run does only what the headline needs: it allocates and warms up the
+registers, times the K steps and prints the result line.  ``ms_per_step`` is
+the wall time of the timed region divided by K.
+
+--dump-outputs DIR writes, after the timed steps, what they computed: every
+seed's final state vector as ``DIR/state_seed<seed>.npy``, float64 of shape
+(amplitudes, 2) = (re, im).  A state that fits the budget (48 MiB over all
+seeds) is written whole; of a larger one, a fixed sample: blocks of 4096
+consecutive amplitudes at block indices drawn once from
+numpy.random.default_rng(DUMP_RNG_SEED) (the same for every seed and every
+run with the same arguments).  The circuits are seeded, so two builds given
+the same arguments can be compared file by file.  Reading a state brings its
+qubits back to their canonical positions, so in a --full run the figures
+measured after the dump on the first seed's register (``unfused_gate_s``,
+``window1_s_per_gate``) start from another layout than without the dump; the
+dump cannot come later, since those measurements change that register.
+
+--full adds, outside the timed region: the norm check of every register
+(``config.norm_error``), one unfused gate (``config.unfused_gate_s``: one
+streaming pass over the state, median of 5) and, on a single GPU (~10 s):
   * ``sweep``: the metric's "vs #qubits" axis -- unfused Hadamard on targets
     0, n/2, n-1 and T on n/2 for n = 20, 22, ..., 32 (median of 5, one
     streaming pass per gate), with the achieved HBM bandwidth;
@@ -42,7 +62,7 @@ Besides the headline, a single-GPU run adds (outside the timed region, ~10 s):
     dephasing, two-qubit dephasing and depolarising per channel, gates;
   * ``fp32``: the headline circuit with the QUEST_PREC=1 library (a child
     process), its s/gate and the ratio to fp64.
-  (--extras q34,fp32 picks some; --no-extras none; the extras use the first seed)
+  (--full --extras q34,fp32 picks some; --full --no-extras none; the extras use the first seed)
 A multi-GPU run must use RCCL (``--allow-transport`` accepts another one).
 """
 from __future__ import annotations
@@ -62,6 +82,10 @@ BASELINE_S_PER_OP = 3783.9266747315614 / 667  # fork's estimate, tutorial_exampl
 
 DEFAULT_SEEDS = "7,11,12,13,17"   # 7: the rounds-1..4 headline; 11-13, 17 never used for tuning
 FUSED_SWEEP_SEEDS = (7, 11, 12, 13, 17)
+ALL_EXTRAS = "window1,fork30,sweep,rotate29,fused_sweep,q34,density17,fp32"
+DUMP_RNG_SEED = 20240607           # --dump-outputs: which blocks of a large state are written
+DUMP_BLOCK = 4096                   # amplitudes per block
+DUMP_BUDGET_BYTES = 48 << 20        # over all seeds (16 bytes per amplitude on disk)
 
 
 def split_layers(circ, n, layers):
@@ -74,6 +98,33 @@ def split_layers(circ, n, layers):
     return out
 
 
+def dump_outputs(qa, regs, seeds, rank, outdir):
+    """Every seed's final state (or a fixed sample of its blocks, see the
+    module docstring) as <outdir>/state_seed<seed>.npy.  Every rank reads
+    (the read is collective), rank 0 writes."""
+    import numpy as np
+
+    if rank == 0:
+        os.makedirs(outdir, exist_ok=True)
+    total = regs[0].num_amps
+    budget = DUMP_BUDGET_BYTES // 16 // max(len(regs), 1)
+    if total <= budget:
+        starts, block = [0], total
+    else:
+        block = DUMP_BLOCK
+        # (at least one block per seed, however many seeds share the budget)
+        picks = np.random.default_rng(DUMP_RNG_SEED).choice(total // block, size=max(1, budget // block), replace=False)
+        starts = [int(b) * block for b in np.sort(picks)]
+    for sd, r in zip(seeds, regs):
+        out = np.empty((len(starts) * block, 2), dtype=np.float64)
+        for i, s0 in enumerate(starts):
+            a = qa.capi.getAmps(r.q, s0, block)
+            out[i * block:(i + 1) * block, 0] = a.real
+            out[i * block:(i + 1) * block, 1] = a.imag
+        if rank == 0:
+            np.save(os.path.join(outdir, f"state_seed{sd}.npy"), out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=int(os.environ.get("WORLD_SIZE", "1")))
@@ -83,16 +134,27 @@ def main():
     ap.add_argument("--eager", action="store_true", help="disable gate fusion (one pass per gate)")
     ap.add_argument("--seeds", default=DEFAULT_SEEDS, help="comma-separated circuit seeds, one window each")
     ap.add_argument("--seed", type=int, default=None, help="a single circuit seed (overrides --seeds)")
-    ap.add_argument("--no-extras", action="store_true", help="skip every extra (single-GPU runs only)")
-    ap.add_argument("--extras", default="window1,fork30,sweep,rotate29,fused_sweep,q34,density17,fp32",
-                    help="comma-separated extras of a single-GPU run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write every seed's final state (or a fixed sample) as DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also, outside the timed region: norm check, one unfused gate and a single-GPU run's extras")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip every extra (single-GPU runs only)")
+    ap.add_argument("--extras", default=None,
+                    help="with --full: comma-separated extras of a single-GPU run (default: " + ALL_EXTRAS + ")")
     ap.add_argument("--allow-transport", action="store_true", help="accept a non-RCCL transport with N > 1")
     args = ap.parse_args()
+    if args.extras is not None and not args.full:
+        ap.error("--extras needs --full")
+    if args.extras is None:
+        args.extras = ALL_EXTRAS
     seeds = [args.seed] if args.seed is not None else [int(x) for x in args.seeds.split(",") if x]
 
     from quest_amd.parallel import allreduce_max, barrier, init_distributed, shutdown
 
     rank, world = init_distributed()
+    if args.no_extras and not args.full and rank == 0:
+        print("bench.py: --no-extras has no effect without --full (a plain run has no extras, and no "
+              "config.norm_error or config.unfused_gate_s either)", file=sys.stderr)
     if world != args.gpus:
         print(f"warning: --gpus {args.gpus} but WORLD_SIZE {world}", file=sys.stderr)
     import torch
@@ -168,34 +230,15 @@ def main():
         prev = (p, sw, by, us, ov)
         seed_rows.append(row)
 
-    reg = regs[0]
-    norm = reg.total_prob()  # sanity (outside the timed region)
-    norm_err = max(abs(r.total_prob() - 1.0) for r in regs)
-    for r in regs[1:]:
-        r.close()
-    # for reference, outside the timed region: one unfused gate (= one full
-    # streaming pass over the state), median of 5
-    qa.capi.setGateFusion(0)
-    singles = []
-    for _ in range(5):
-        reg.sync()
-        t1 = time.perf_counter()
-        reg.h(n // 2)
-        reg.sync()
-        singles.append(time.perf_counter() - t1)
-    qa.capi.setGateFusion(1)
-    unfused_gate_s = allreduce_max(sorted(singles)[2])
-    s_per_gate = elapsed / max(gates, 1)
-    extras = {}
-    if world == 1 and not args.no_extras and qa.capi.getQuESTBackend() == "HIP":
-        try:
-            extras = run_extras(qa, reg, n, per_seed_layers[0], args, seeds[0])   # closes reg
-        except Exception as e:  # an optional extra must never cost the headline
-            extras = {"extras_error": f"{type(e).__name__}: {e}"[:500]}
-        if "s_per_gate" in extras.get("fp32", {}):
-            extras["fp32"]["ratio_to_fp64"] = extras["fp32"]["s_per_gate"] / seed_rows[0]["s_per_gate"]
+    if args.dump_outputs:
+        dump_outputs(qa, regs, seeds, rank, args.dump_outputs)
+    full = {}
+    if args.full:
+        full = run_full(qa, regs, n, per_seed_layers[0], args, seeds[0], world, seed_rows)   # closes the registers
     else:
-        reg.close()
+        for r in regs:
+            r.close()
+    s_per_gate = elapsed / max(gates, 1)
     multi = {}
     if world > 1:
         swap_ms = sum(r["swap_ms"] for r in seed_rows)
@@ -238,15 +281,48 @@ def main():
             "passes_per_seed": stats["passes"] / len(seeds),
             "swaps": stats["swaps"],
             **multi,
-            "norm_error": max(abs(norm - 1.0), norm_err),
-            "unfused_gate_s": unfused_gate_s,
             "backend": qa.capi.getQuESTBackend(),
-            **extras,
+            **full,
         },
     }
     if rank == 0:
         print(json.dumps(result), flush=True)
     shutdown()
+
+
+def run_full(qa, regs, n, layer_gates, args, seed, world, seed_rows):
+    """--full: the norm check, one unfused gate and a single-GPU run's extras,
+    all outside the timed region; closes the registers."""
+    from quest_amd.parallel import allreduce_max
+
+    reg = regs[0]
+    norm = reg.total_prob()  # sanity (outside the timed region)
+    norm_err = max(abs(r.total_prob() - 1.0) for r in regs)
+    for r in regs[1:]:
+        r.close()
+    # for reference, outside the timed region: one unfused gate (= one full
+    # streaming pass over the state), median of 5
+    qa.capi.setGateFusion(0)
+    singles = []
+    for _ in range(5):
+        reg.sync()
+        t1 = time.perf_counter()
+        reg.h(n // 2)
+        reg.sync()
+        singles.append(time.perf_counter() - t1)
+    qa.capi.setGateFusion(1)
+    unfused_gate_s = allreduce_max(sorted(singles)[2])
+    extras = {}
+    if world == 1 and not args.no_extras and qa.capi.getQuESTBackend() == "HIP":
+        try:
+            extras = run_extras(qa, reg, n, layer_gates, args, seed)   # closes reg
+        except Exception as e:  # an optional extra must never cost the headline
+            extras = {"extras_error": f"{type(e).__name__}: {e}"[:500]}
+        if "s_per_gate" in extras.get("fp32", {}):
+            extras["fp32"]["ratio_to_fp64"] = extras["fp32"]["s_per_gate"] / seed_rows[0]["s_per_gate"]
+    else:
+        reg.close()
+    return {"norm_error": max(abs(norm - 1.0), norm_err), "unfused_gate_s": unfused_gate_s, **extras}
 
 
 def _median_time(fn, reps=5):
@@ -359,7 +435,7 @@ def _run_fp32(args, seed):
     process binds one native library)."""
     import subprocess
 
-    cmd = [sys.executable, os.path.abspath(__file__), "--no-extras", "--steps", str(args.steps), "--warmup",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-extras", "--steps", str(args.steps), "--warmup",
            str(args.warmup), "--qubits", str(args.qubits), "--seed", str(seed)]
     env = dict(os.environ, QUEST_PREC="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):

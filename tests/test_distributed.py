@@ -183,7 +183,7 @@ def test_bench_under_torchrun_host_build():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4", "--master-addr",
            "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "4", "--qubits", "14", "--steps", "3",
-           "--warmup", "1", "--allow-transport"]
+           "--warmup", "1", "--allow-transport", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -36,7 +36,7 @@ def test_bench_under_torchrun_ipc(ranks):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", str(ranks),
-           "--qubits", "22", "--steps", "4", "--warmup", "1", "--allow-transport"]
+           "--qubits", "22", "--steps", "4", "--warmup", "1", "--allow-transport", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -66,7 +66,7 @@ def test_bench_under_torchrun_rccl_shared_gpu(ranks):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", str(ranks),
-           "--qubits", "22", "--steps", "4", "--warmup", "1"]
+           "--qubits", "22", "--steps", "4", "--warmup", "1", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

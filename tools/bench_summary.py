@@ -17,7 +17,8 @@ def main():
     d = load(sys.argv[1])
     c = d["config"]
     print(f"value {d['value'] * 1e3:.4f} ms/gate  n_gpus {d['n_gpus']}  passes {c['passes']} "
-          f"({c.get('passes_per_seed', 0):.1f} per seed)  norm_err {c['norm_error']:.1e}")
+          f"({c.get('passes_per_seed', 0):.1f} per seed)" +
+          (f"  norm_err {c['norm_error']:.1e}" if "norm_error" in c else ""))   # (a --full run has it)
     for r in c.get("seeds", []):
         extra = ""
         if "swap_ms" in r:

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/mem_path_ab.txt
 : > $OUT
 for round in 1 2; do
   for v in "" "QUEST_WAVE_TILE_MAP=1" "QUEST_WAVE_WG_PER_CU=2" "QUEST_WAVE_WG_PER_CU=3" "QUEST_WAVE_WG_PER_CU=4"; do
-    line=$(env QUEST_WAVE_NOOPS=1 $v timeout -k 10 120 python3 $R/bench.py --no-extras --steps 20 --warmup 5) || exit $?
+    line=$(env QUEST_WAVE_NOOPS=1 $v timeout -k 10 120 python3 $R/bench.py --full --no-extras --steps 20 --warmup 5) || exit $?
     echo "$line" | python3 -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][0]); c=d['config']

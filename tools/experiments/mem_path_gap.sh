@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/mem_path_gap.txt
 for round in 1 2; do
   IFS=';' read -ra VS <<< "${VARIANTS:-QUEST_WAVE_NOOPS=1;QUEST_WAVE_NOOPS=1 QUEST_IM_GAP=8589934592;QUEST_WAVE_NOOPS=0;QUEST_WAVE_NOOPS=0 QUEST_IM_GAP=8589934592}"
   for v in "${VS[@]}"; do
-    line=$(env $v timeout -k 10 150 python3 $R/bench.py --no-extras --seeds ${SEEDS:-7,12} --steps 10 --warmup 3) || exit $?
+    line=$(env $v timeout -k 10 150 python3 $R/bench.py --full --no-extras --seeds ${SEEDS:-7,12} --steps 10 --warmup 3) || exit $?
     echo "$line" | python3 -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); c=d['config']

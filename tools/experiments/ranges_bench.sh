@@ -5,7 +5,7 @@ set -o pipefail
 for ranks in 2 4; do
   for rf in 1 0; do
     QUEST_SWAP_RANGES_FIRST=$rf QUEST_RCCL_SHARED_GPU=1 QUEST_COMM_TIMEOUT=150 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node=$ranks \
-      --master-addr 127.0.0.1 --master-port $((29700 + ranks + 10 * rf)) bench.py --gpus $ranks --qubits 25 --steps 20 --warmup 5 --no-extras \
+      --master-addr 127.0.0.1 --master-port $((29700 + ranks + 10 * rf)) bench.py --gpus $ranks --qubits 25 --steps 20 --warmup 5 --full --no-extras \
       > gpurun_out/rb.json 2> gpurun_out/rb.err || { tail -20 gpurun_out/rb.err; exit 1; }
     python3 -c "
 import json; d=json.loads([l for l in open('gpurun_out/rb.json') if l.startswith('{')][0]); c=d['config']
