@@ -37,7 +37,7 @@ COMMON_SRC := src/api/api.cpp src/api/validation.cpp src/api/qasm.cpp src/api/co
               src/api/mt19937.cpp src/core/router.cpp src/core/tiles.cpp src/core/wave.cpp src/core/wave_emu.cpp src/core/trace.cpp src/comm/bootstrap.cpp
 CPU_SRC    := $(COMMON_SRC) src/comm/comm_socket.cpp src/comm/comm_host.cpp src/cpu/backend_cpu.cpp
 HIP_HOST   := $(COMMON_SRC) src/comm/comm_socket.cpp src/comm/comm_rccl.cpp src/comm/comm_ipc.cpp
-HIP_DEV    := src/hip/backend_hip.hip src/hip/kernels_gates.hip src/hip/kernels_direct.hip src/hip/kernels_reduce.hip src/hip/kernels_misc.hip
+HIP_DEV    := src/hip/backend_hip.hip src/hip/kernels_gates.hip src/hip/kernels_direct.hip src/hip/kernels_reduce.hip src/hip/kernels_pauli.hip src/hip/kernels_misc.hip
 
 INCLUDES   := -Iinclude -DQA_WAVE_SLOTS_F64=$(strip $(WAVE_SLOTS)) -DQA_WAVE_SLOTS_F32=$(strip $(WAVE_SLOTS32)) \
               -DQA_WAVE_WBITS_F64=$(strip $(WAVE_WBITS)) -DQA_WAVE_WBITS_F32=$(strip $(WAVE_WBITS32))

@@ -123,6 +123,44 @@ void canonicaliseQureg(Qureg qureg);
 /* physical bit position of each logical qubit of the state-vector */
 void getQubitLayout(Qureg qureg, int* physicalOfLogical);
 
+/* ---- Pauli expectation values ------------------------------------------------
+ * <psi| P |psi> (state-vectors) or Tr(P rho) (density matrices) of Pauli
+ * strings P, read from the register in one streaming pass: no second register,
+ * nothing written.  Names and argument order are QuEST v3's.  Collective.
+ *
+ * `workspace` is accepted for source compatibility only: it must have the type
+ * and dimensions of `qureg` (E_MISMATCHING_QUREG_TYPES / _DIMENSIONS) but is
+ * never read or written; passing `qureg` itself is allowed.
+ *
+ * The terms of a sum share passes: a pass loads tiles of
+ * 2^QUEST_PAULI_TILE_QUBITS amplitudes that hold the lowest
+ * QUEST_PAULI_TILE_LOW_QUBITS positions plus up to
+ * (QUEST_PAULI_TILE_QUBITS - QUEST_PAULI_TILE_LOW_QUBITS) further positions,
+ * and evaluates up to QUEST_PAULI_MAX_TERMS_PER_PASS terms whose X / Y qubits
+ * all sit on those positions.  Terms are grouped greedily, first fit in term
+ * order: first the terms with an X or Y, then the pure Z / I strings (which fit
+ * any group with room).  A term with X / Y on more positions than a tile holds
+ * takes a pass of its own.
+ *
+ * Errors besides the usual target checks: E_INVALID_PAULI_CODE (33),
+ * E_INVALID_NUM_TARGETS (34), E_INVALID_NUM_SUM_TERMS (35) and, on a
+ * distributed state-vector, E_PAULI_TOO_WIDE_FOR_RANKS (36) for a string with
+ * X / Y on more qubits than one rank's chunk holds. */
+enum pauliOpType { PAULI_I = 0, PAULI_X = 1, PAULI_Y = 2, PAULI_Z = 3 };
+#define QUEST_PAULI_TILE_QUBITS 12
+#define QUEST_PAULI_TILE_LOW_QUBITS 5
+#define QUEST_PAULI_MAX_TERMS_PER_PASS 16
+
+/* Expectation of the product of pauliCodes[i] on targetQubits[i] (distinct). */
+qreal calcExpecPauliProd(Qureg qureg, int* targetQubits, enum pauliOpType* pauliCodes, int numTargets,
+                         Qureg workspace);
+/* sum_t termCoeffs[t] <P_t>; allPauliCodes holds numSumTerms x
+ * numQubitsRepresented codes, term-major, qubit 0 first. */
+qreal calcExpecPauliSum(Qureg qureg, enum pauliOpType* allPauliCodes, qreal* termCoeffs, int numSumTerms,
+                        Qureg workspace);
+/* Extension: termExpecs[t] = <P_t> of every term (allPauliCodes as above). */
+void calcExpecPauliTerms(Qureg qureg, enum pauliOpType* allPauliCodes, int numSumTerms, qreal* termExpecs);
+
 typedef struct QuESTStats {
     long long opsQueued;      /* elementary ops accepted by the backend */
     long long passes;         /* passes over the state (kernel launches of gate kernels) */
@@ -149,6 +187,8 @@ typedef struct QuESTStats {
     long long overlappedPasses; /* passes started on the part of the chunk a swap in flight leaves in place */
     long long layoutAligns;   /* swaps / chunk restores before which this rank moved its local qubits to rank 0's positions */
     long long placementProbes; /* re / im placements measured by the allocation probe (HIP; 1 when a remembered one was taken) */
+    long long pauliPasses;    /* passes over the state made for Pauli expectation values (each also counts in reductions) */
+    long long pauliTerms;     /* Pauli strings evaluated by them */
 } QuESTStats;
 void getQuESTStats(QuESTStats* stats);
 void resetQuESTStats(void);

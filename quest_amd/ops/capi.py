@@ -84,7 +84,8 @@ class _Binding:
                          "verifiedFlushes", "wavePasses", "waveOps", "waveTransposes", "relabels",
                          "globalDiags", "flushes", "marginalPasses", "waveShadowChecks",
                          "waveShadowMismatches", "permutedOps", "relayouts", "restoreRounds", "swapMicros",
-                         "overlappedSwaps", "overlappedPasses", "layoutAligns", "placementProbes")]
+                         "overlappedSwaps", "overlappedPasses", "layoutAligns", "placementProbes",
+                         "pauliPasses", "pauliTerms")]
 
         self.Complex, self.ComplexMatrix2, self.Vector = Complex, ComplexMatrix2, Vector
         self.ComplexArray, self.QASMLogger, self.Qureg = ComplexArray, QASMLogger, Qureg
@@ -152,6 +153,9 @@ class _Binding:
             "getQubitLayout": (v, [Q, ip]), "getAmps": (v, [Q, ll, rp, rp, ll]), "getQuESTStats": (v, [P(QuESTStats)]), "resetQuESTStats": (v, []),
             "getQuESTBackend": (C.c_char_p, []), "getQuESTTransport": (C.c_char_p, []), "getQuESTSeeds": (v, [P(C.c_ulong), ip]),
             "saveQuregCheckpoint": (i, [Q, C.c_char_p]), "loadQuregCheckpoint": (i, [Q, C.c_char_p]),
+            # Pauli expectation values (enum pauliOpType is an int)
+            "calcExpecPauliProd": (r, [Q, ip, ip, i, Q]), "calcExpecPauliSum": (r, [Q, ip, rp, i, Q]),
+            "calcExpecPauliTerms": (v, [Q, ip, i, rp]),
         }
         for name, (res, args) in self.protos.items():
             f = getattr(lib, name)
@@ -452,6 +456,46 @@ def getAmps(q, startInd=0, numAmps=None):
     _call("getAmps", q, startInd, re.ctypes.data_as(C.POINTER(b.qreal)), im.ctypes.data_as(C.POINTER(b.qreal)),
           numAmps)
     return re.astype(np.float64) + 1j * im.astype(np.float64)
+
+
+# enum pauliOpType and the tile capacity of the batched pass (quest_amd.h)
+PAULI_I, PAULI_X, PAULI_Y, PAULI_Z = 0, 1, 2, 3
+PAULI_TILE_QUBITS = 12
+PAULI_TILE_LOW_QUBITS = 5
+PAULI_MAX_TERMS_PER_PASS = 16
+
+
+def calcExpecPauliProd(q, targetQubits, pauliCodes, numTargets=None, workspace=None) -> float:
+    """<P> of the product of pauliCodes[i] on targetQubits[i]; the workspace
+    (never touched by the library) defaults to the register itself."""
+    b = binding()
+    if numTargets is None:
+        numTargets = len(targetQubits)
+    return float(_call("calcExpecPauliProd", q, b.int_array(targetQubits), b.int_array(pauliCodes), numTargets,
+                       q if workspace is None else workspace))
+
+
+def calcExpecPauliSum(q, allPauliCodes, termCoeffs, numSumTerms=None, workspace=None) -> float:
+    """sum_t termCoeffs[t] <P_t>; allPauliCodes is numSumTerms x numQubits, flat
+    or nested, qubit 0 first."""
+    b = binding()
+    codes = np.asarray(allPauliCodes, dtype=np.int64).reshape(-1)
+    ca, cp = b.real_array(termCoeffs)
+    if numSumTerms is None:
+        numSumTerms = len(ca)
+    return float(_call("calcExpecPauliSum", q, b.int_array(codes), cp, numSumTerms,
+                       q if workspace is None else workspace))
+
+
+def calcExpecPauliTerms(q, allPauliCodes, numSumTerms=None) -> np.ndarray:
+    """<P_t> of every term as a float64 array (allPauliCodes as calcExpecPauliSum)."""
+    b = binding()
+    codes = np.asarray(allPauliCodes, dtype=np.int64).reshape(-1)
+    if numSumTerms is None:
+        numSumTerms = len(codes) // q.numQubitsRepresented
+    out = np.zeros(max(int(numSumTerms), 0), dtype=b.np_real)
+    _call("calcExpecPauliTerms", q, b.int_array(codes), numSumTerms, out.ctypes.data_as(C.POINTER(b.qreal)))
+    return out.astype(np.float64)
 
 
 def getQuESTStats() -> dict:

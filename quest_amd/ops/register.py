@@ -257,6 +257,37 @@ class Register:
     def inner(self, ket: "Register") -> complex:
         return capi.calcInnerProduct(self.q, ket.q)
 
+    # -- Pauli expectation values ----------------------------------------------
+    def _pauli_codes(self, term) -> list:
+        """One term as numQubits codes: a string over IXYZ, qubit 0 first
+        (shorter strings are padded with I), or a {qubit: 'X'|'Y'|'Z'} dict."""
+        n = self.num_qubits
+        codes = [0] * n
+        items = term.items() if isinstance(term, dict) else enumerate(term)
+        for qubit, p in items:
+            qubit = int(qubit)
+            if not 0 <= qubit < n:
+                raise ValueError(f"Pauli term {term!r}: qubit {qubit} outside the {n}-qubit register")
+            try:
+                codes[qubit] = "IXYZ".index(str(p).upper())
+            except ValueError:
+                raise ValueError(f"Pauli term {term!r}: {p!r} is not one of I, X, Y, Z") from None
+        return codes
+
+    def expec_pauli(self, paulis) -> float:
+        """<P> of one Pauli string (one read-only pass, no second register)."""
+        return float(self.expec_pauli_terms([paulis])[0])
+
+    def expec_pauli_terms(self, terms) -> np.ndarray:
+        """<P_t> of every term; the terms share passes over the state."""
+        codes = [self._pauli_codes(t) for t in terms]
+        return capi.calcExpecPauliTerms(self.q, codes, len(codes))
+
+    def expec_pauli_sum(self, terms, coeffs) -> float:
+        """sum_t coeffs[t] <P_t>."""
+        codes = [self._pauli_codes(t) for t in terms]
+        return capi.calcExpecPauliSum(self.q, codes, coeffs, len(codes))
+
     def amp(self, index) -> complex:
         return capi.getAmp(self.q, index)
 

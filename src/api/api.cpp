@@ -775,6 +775,81 @@ qreal calcFidelity(Qureg qureg, Qureg pureState) {
     return ip.re * ip.re + ip.im * ip.im;
 }
 
+// ---- Pauli expectation values (quest_amd.h) -----------------------------------
+// Terms as (x, z, nY) masks over logical qubits; reads only: the queue is
+// flushed, nothing is recorded as QASM and the state generation stays.
+namespace {
+struct PauliTerms {
+    std::vector<u64> x, z;
+    std::vector<int> nY;
+    void add(int qubit, int code) {
+        if (code == PAULI_X || code == PAULI_Y) x.back() |= 1ull << qubit;
+        if (code == PAULI_Z || code == PAULI_Y) z.back() |= 1ull << qubit;
+        if (code == PAULI_Y) nY.back()++;
+    }
+    void begin() {
+        x.push_back(0);
+        z.push_back(0);
+        nY.push_back(0);
+    }
+};
+
+// every string's X / Y qubits must fit one chunk of a distributed state-vector
+bool pauliTermsFit(const QuregImpl& q, const PauliTerms& t, const char* f) {
+    if (q.isDensity || q.numChunks == 1) return true;
+    for (u64 x : t.x)
+        if (!v::pauliFitsRanks(__builtin_popcountll(x), q.L, f)) return false;
+    return true;
+}
+
+bool pauliSumTerms(Qureg qureg, const int* codes, int numSumTerms, PauliTerms& t, const char* f) {
+    if (!v::numSumTerms(numSumTerms, f)) return false;
+    const int n = qureg.numQubitsRepresented;
+    if (!v::pauliCodes(codes, (long long)numSumTerms * n, f)) return false;
+    for (int s = 0; s < numSumTerms; s++) {
+        t.begin();
+        for (int j = 0; j < n; j++) t.add(j, codes[(size_t)s * n + j]);
+    }
+    return pauliTermsFit(Q(qureg), t, f);
+}
+}  // namespace
+
+qreal calcExpecPauliProd(Qureg qureg, int* targetQubits, enum pauliOpType* pauliCodes, int numTargets,
+                         Qureg workspace) {
+    const int* codes = reinterpret_cast<const int*>(pauliCodes);
+    if (!v::matchingTypes(qureg, workspace, __func__) || !v::matchingDims(qureg, workspace, __func__) ||
+        !v::multiTargets(qureg, targetQubits, numTargets, __func__) || !v::pauliCodes(codes, numTargets, __func__))
+        return 0;
+    PauliTerms t;
+    t.begin();
+    for (int i = 0; i < numTargets; i++) t.add(targetQubits[i], codes[i]);
+    QuregImpl& q = Q(qureg);
+    if (!pauliTermsFit(q, t, __func__)) return 0;
+    double e;
+    router::pauliExpec(q, 1, t.x.data(), t.z.data(), t.nY.data(), &e);
+    return (qreal)e;
+}
+
+void calcExpecPauliTerms(Qureg qureg, enum pauliOpType* allPauliCodes, int numSumTerms, qreal* termExpecs) {
+    PauliTerms t;
+    if (!pauliSumTerms(qureg, reinterpret_cast<const int*>(allPauliCodes), numSumTerms, t, __func__)) return;
+    std::vector<double> e((size_t)numSumTerms);
+    router::pauliExpec(Q(qureg), numSumTerms, t.x.data(), t.z.data(), t.nY.data(), e.data());
+    for (int s = 0; s < numSumTerms; s++) termExpecs[s] = (qreal)e[(size_t)s];
+}
+
+qreal calcExpecPauliSum(Qureg qureg, enum pauliOpType* allPauliCodes, qreal* termCoeffs, int numSumTerms,
+                        Qureg workspace) {
+    if (!v::matchingTypes(qureg, workspace, __func__) || !v::matchingDims(qureg, workspace, __func__)) return 0;
+    PauliTerms t;
+    if (!pauliSumTerms(qureg, reinterpret_cast<const int*>(allPauliCodes), numSumTerms, t, __func__)) return 0;
+    std::vector<double> e((size_t)numSumTerms);
+    router::pauliExpec(Q(qureg), numSumTerms, t.x.data(), t.z.data(), t.nY.data(), e.data());
+    double sum = 0;
+    for (int s = 0; s < numSumTerms; s++) sum += (double)termCoeffs[s] * e[(size_t)s];
+    return (qreal)sum;
+}
+
 void addDensityMatrix(Qureg combineQureg, qreal otherProb, Qureg otherQureg) {
     if (!v::densMatr(combineQureg, __func__) || !v::densMatr(otherQureg, __func__) ||
         !v::matchingDims(combineQureg, otherQureg, __func__) || !v::prob(otherProb, __func__))
@@ -1202,6 +1277,8 @@ void getQuESTStats(QuESTStats* s) {
     s->overlappedPasses = stats().overlappedPasses;
     s->layoutAligns = stats().layoutAligns;
     s->placementProbes = stats().placementProbes;
+    s->pauliPasses = stats().pauliPasses;
+    s->pauliTerms = stats().pauliTerms;
 }
 
 void resetQuESTStats(void) {

@@ -46,6 +46,10 @@ static const char* kMessages[E_NUM_ERROR_CODES] = {
     "Out of device memory while allocating the register.",
     "Device runtime error.",
     "Checkpoint does not match the register (number of qubits, register type or precision).",
+    "Invalid Pauli code. Must be 0 (PAULI_I), 1 (PAULI_X), 2 (PAULI_Y) or 3 (PAULI_Z).",
+    "Invalid number of target qubits. Must be >0 and <=numQubits.",
+    "Invalid number of terms in the Pauli sum. Must be >0.",
+    "The Pauli string has X or Y on more qubits than one rank's chunk holds.",
 };
 
 static QuESTErrorHandler g_handler = nullptr;
@@ -185,6 +189,26 @@ bool oneQubitDampingProb(qreal p, const char* f) {
 }
 bool twoQubitDepolProb(qreal p, const char* f) {
     return prob(p, f) && check(p <= 15 / 16.0, E_INVALID_TWO_QUBIT_DEPOL_PROB, f);
+}
+
+bool multiTargets(const Qureg& q, const int* targets, int n, const char* f) {
+    if (!check(n > 0 && n <= q.numQubitsRepresented, E_INVALID_NUM_TARGETS, f)) return false;
+    unsigned long long seen = 0;
+    for (int i = 0; i < n; i++) {
+        if (!target(q, targets[i], f)) return false;
+        if (!check(!((seen >> targets[i]) & 1), E_TARGETS_NOT_UNIQUE, f)) return false;
+        seen |= 1ull << targets[i];
+    }
+    return true;
+}
+bool pauliCodes(const int* codes, long long n, const char* f) {
+    for (long long i = 0; i < n; i++)
+        if (!check(codes[i] >= 0 && codes[i] <= 3, E_INVALID_PAULI_CODE, f)) return false;
+    return true;
+}
+bool numSumTerms(int n, const char* f) { return check(n > 0, E_INVALID_NUM_SUM_TERMS, f); }
+bool pauliFitsRanks(int numXY, int numLocal, const char* f) {
+    return check(numXY <= numLocal, E_PAULI_TOO_WIDE_FOR_RANKS, f);
 }
 
 }  // namespace v

@@ -45,6 +45,11 @@ enum ErrorCode {
     E_OUT_OF_MEMORY,
     E_DEVICE_ERROR,
     E_CHECKPOINT_MISMATCH,
+    // Pauli expectation values (quest_amd.h)
+    E_INVALID_PAULI_CODE,
+    E_INVALID_NUM_TARGETS,
+    E_INVALID_NUM_SUM_TERMS,
+    E_PAULI_TOO_WIDE_FOR_RANKS,
     E_NUM_ERROR_CODES
 };
 
@@ -80,6 +85,12 @@ bool twoQubitDephaseProb(qreal p, const char* f);
 bool oneQubitDepolProb(qreal p, const char* f);
 bool oneQubitDampingProb(qreal p, const char* f);
 bool twoQubitDepolProb(qreal p, const char* f);
+// targets[0..n): n in [1, numQubitsRepresented], each in range, all distinct
+bool multiTargets(const Qureg& q, const int* targets, int n, const char* f);
+bool pauliCodes(const int* codes, long long n, const char* f);
+bool numSumTerms(int n, const char* f);
+// the X / Y qubits of one Pauli string must fit a rank's chunk (numLocal qubits)
+bool pauliFitsRanks(int numXY, int numLocal, const char* f);
 }  // namespace v
 
 }  // namespace qa

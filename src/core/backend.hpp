@@ -9,6 +9,7 @@
 #pragma once
 
 #include "core.hpp"
+#include "quest_amd.h"
 
 namespace qa {
 namespace be {
@@ -71,6 +72,24 @@ void innerProductPerm(QuregImpl& bra, QuregImpl& ket, const int* sig, double out
 // physical flat index of rho(r,r) is sum_{j : bit j of r} offs[j]; only
 // indices inside [chunkStart, chunkStart + numAmpsPerChunk) contribute.
 double densDiagSum(QuregImpl& q, const u64* offs, int n, int skipBit, i64 chunkStart);
+// Pauli strings, nTerms <= kPauliMaxTerms in one pass over the chunk.
+// per term t < nTerms: out[2t], out[2t+1] = Re, Im of  sum_i (-1)^popcount(i & z[t]) conj(a[i ^ x[t]]) a[i]
+// over this chunk; every bit of every x[t] is a local position.  (The pairs
+// i, i ^ x[t] make the sum real when popcount(x[t] & z[t]) is even and
+// imaginary when it is odd: only that part is computed, the other is 0.)
+// HIP: the tile kernel when the chunk has kPauliTileBits positions and the
+// terms' x bits above the lowest kPauliLowBits positions number at most
+// kPauliTileBits - kPauliLowBits (router batching), else the generic kernel,
+// which re-streams the chunk per term.
+constexpr int kPauliTileBits = QUEST_PAULI_TILE_QUBITS;
+constexpr int kPauliLowBits = QUEST_PAULI_TILE_LOW_QUBITS;
+constexpr int kPauliMaxTerms = QUEST_PAULI_MAX_TERMS_PER_PASS;
+void pauliExpec(QuregImpl& q, int nTerms, const u64* x, const u64* z, double* out);
+// density: sum over logical rows i of (-1)^popcount(i & z[t]) rho(i, i ^ x[t]), elements inside the chunk only.
+// The physical flat index of rho(r, c) is sum_{j : bit j of r} rowOffs[j] + sum_{j : bit j of c} colOffs[j];
+// nTerms <= kPauliMaxTerms, out[2t], out[2t+1] = Re, Im
+void densPauliExpec(QuregImpl& q, const u64* rowOffs, const u64* colOffs, int n, i64 chunkStart,
+                    int nTerms, const u64* x, const u64* z, double* out);
 
 // ---- non-unitary local ops --------------------------------------------------
 // a := alpha a + beta b

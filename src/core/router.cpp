@@ -1396,6 +1396,150 @@ double densFidelity(QuregImpl& rho, QuregImpl& psi) {
     return allSum(part);
 }
 
+// ---- Pauli expectation values ---------------------------------------------------
+// <psi|P|psi> = Re(i^nY sum_i (-1)^popcount(i & z) conj(a[i ^ x]) a[i]): one
+// read-only stream of the state per batch of terms (be::pauliExpec), no second
+// register.  The reference's route (v3 calcExpecPauliProd) clones the state,
+// applies the Paulis to the clone and takes an inner product.
+namespace {
+
+// Bring the logical qubits in `need` (at most q.L of them) onto local positions
+// with the swap a gate on them would cause: a synthetic queue of one-qubit
+// dense ops, those on rank positions first.  The layout changes, the logical
+// state does not.  Collective; the decision depends on the layout only.
+void localise(QuregImpl& q, u64 need) {
+    for (int round = 0; round < 64; round++) {
+        std::vector<Op> lq;
+        for (int pass = 0; pass < 2; pass++)
+            for (int lg = 0; lg < q.nSV; lg++) {
+                if (!((need >> lg) & 1) || (q.l2p[lg] >= q.L) != (pass == 0)) continue;
+                Op op;
+                op.kind = OpKind::Mat2;
+                op.nt = 1;
+                op.t[0] = lg;
+                for (int e = 0; e < 4; e++) op.m[e] = {(real)0.5, 0};   // dense: its target must be local
+                lq.push_back(op);
+            }
+        if (lq.empty() || q.l2p[lq[0].t[0]] < q.L) return;
+        planSwap(q, lq);
+    }
+    fprintf(stderr, "QuEST: could not bring the qubits of a Pauli string onto one rank\n");
+    exit(EXIT_FAILURE);
+}
+
+// value of one term from the chunk sums (re, im): Re(i^nY (re + i im))
+inline double pauliValue(int nY, double re, double im) {
+    switch (nY & 3) {
+    case 0: return re;
+    case 1: return -im;
+    case 2: return -re;
+    default: return im;
+    }
+}
+
+// State-vector terms [t0, t1) whose X / Y qubits are all local: physical
+// masks, the sign of Z on rank positions, batches, one backend call per batch.
+void pauliLocalTerms(QuregImpl& q, int t0, int t1, const u64* lx, const u64* lz, const int* nY, double* val) {
+    const int T = t1 - t0;
+    std::vector<u64> px((size_t)T, 0), pz((size_t)T, 0);
+    std::vector<int> neg((size_t)T, 0);
+    for (int t = 0; t < T; t++)
+        for (int lg = 0; lg < q.nSV; lg++) {
+            const int p = q.l2p[lg];
+            if ((lx[t0 + t] >> lg) & 1) px[(size_t)t] |= 1ull << p;
+            if (!((lz[t0 + t] >> lg) & 1)) continue;
+            if (p < q.L)
+                pz[(size_t)t] |= 1ull << p;
+            else
+                neg[(size_t)t] ^= chunkBit(q, p);
+        }
+    // Batches (quest_amd.h): greedy first fit in term order, the terms with an
+    // X or Y first -- a batch takes a term while the union of the X / Y
+    // positions above the always-resident low ones fits the tile and it has
+    // room --, then the pure Z / I strings into any batch with room.  A chunk
+    // smaller than a tile goes to the generic kernel, which takes any x.
+    struct Batch {
+        u64 hi = 0;
+        std::vector<int> terms;
+    };
+    std::vector<Batch> batches;
+    const bool tiled = q.L >= be::kPauliTileBits;
+    const u64 lowMask = (1ull << be::kPauliLowBits) - 1;
+    const int cap = be::kPauliTileBits - be::kPauliLowBits;
+    for (int phase = 0; phase < 2; phase++)
+        for (int t = 0; t < T; t++) {
+            const u64 hi = tiled ? px[(size_t)t] & ~lowMask : 0;
+            if ((px[(size_t)t] != 0) != (phase == 0)) continue;
+            Batch* dst = nullptr;
+            for (Batch& b : batches)
+                if ((int)b.terms.size() < be::kPauliMaxTerms && __builtin_popcountll(b.hi | hi) <= cap) {
+                    dst = &b;
+                    break;
+                }
+            if (!dst) {   // (a term wider than the tile: alone, its batch takes nothing else)
+                batches.emplace_back();
+                dst = &batches.back();
+            }
+            dst->hi |= hi;
+            dst->terms.push_back(t);
+        }
+    for (const Batch& b : batches) {
+        const int n = (int)b.terms.size();
+        u64 bx[be::kPauliMaxTerms], bz[be::kPauliMaxTerms];
+        double o[2 * be::kPauliMaxTerms];
+        for (int k = 0; k < n; k++) {
+            bx[k] = px[(size_t)b.terms[(size_t)k]];
+            bz[k] = pz[(size_t)b.terms[(size_t)k]];
+        }
+        stats().reductions++;
+        stats().pauliPasses++;
+        be::pauliExpec(q, n, bx, bz, o);
+        for (int k = 0; k < n; k++) {
+            const int t = b.terms[(size_t)k];
+            const double v = pauliValue(nY[t0 + t], o[2 * k], o[2 * k + 1]);
+            val[t0 + t] = neg[(size_t)t] ? -v : v;
+        }
+    }
+}
+
+}  // namespace
+
+void pauliExpec(QuregImpl& q, int nTerms, const u64* x, const u64* z, const int* nY, double* out) {
+    drain(q);
+    stats().pauliTerms += nTerms;
+    if (q.isDensity) {
+        // Tr(P rho) = Re(i^nY sum_i (-1)^popcount(i & z) rho(i, i ^ x)): 2^n of
+        // the 4^n elements, wherever they sit (densDiag's addressing)
+        u64 rowOffs[64], colOffs[64];
+        for (int j = 0; j < q.nRep; j++) {
+            rowOffs[j] = 1ull << q.l2p[j];
+            colOffs[j] = 1ull << q.l2p[j + q.nRep];
+        }
+        for (int t0 = 0; t0 < nTerms; t0 += be::kPauliMaxTerms) {
+            const int n = std::min(be::kPauliMaxTerms, nTerms - t0);
+            double o[2 * be::kPauliMaxTerms];
+            stats().reductions++;
+            stats().pauliPasses++;
+            be::densPauliExpec(q, rowOffs, colOffs, q.nRep, (i64)q.chunkId * q.numAmpsPerChunk, n, x + t0, z + t0, o);
+            for (int k = 0; k < n; k++) out[t0 + k] = pauliValue(nY[t0 + k], o[2 * k], o[2 * k + 1]);
+        }
+    } else {
+        // runs of consecutive terms whose X / Y qubits fit one chunk together:
+        // one swap (if any) per run -- one for the whole call unless the terms
+        // carry X / Y on more than q.L qubits between them
+        int t0 = 0;
+        while (t0 < nTerms) {
+            u64 need = x[t0];
+            int t1 = t0 + 1;
+            while (t1 < nTerms && __builtin_popcountll(need | x[t1]) <= q.L) need |= x[t1++];
+            if (distributed(q)) localise(q, need);
+            pauliLocalTerms(q, t0, t1, x, z, nY, out);
+            t0 = t1;
+        }
+    }
+    if (comm::active()) comm::allreduceSum(out, nTerms);
+}
+
 void readChunk(QuregImpl& q, real* re, real* im) {
     canonicalise(q);
     be::readAmps(q, 0, re, im, q.numAmpsPerChunk);

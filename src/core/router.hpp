@@ -76,6 +76,12 @@ double densProbZero(QuregImpl& q, int qubit);
 double densTrace(QuregImpl& q);
 cplx inner(QuregImpl& bra, QuregImpl& ket);
 double densFidelity(QuregImpl& rho, QuregImpl& psi);
+// Expectation values of nTerms Pauli strings, term t given by its logical
+// masks x[t] (qubits carrying X or Y), z[t] (Z or Y) and the number nY[t] of
+// Y's: out[t] = <psi|P_t|psi> or Tr(P_t rho), the same on every rank.  Terms
+// share passes over the state (be::pauliExpec batches); one allreduce.  On a
+// distributed state-vector every x[t] has at most q.L bits (API check).
+void pauliExpec(QuregImpl& q, int nTerms, const u64* x, const u64* z, const int* nY, double* out);
 // read this rank's chunk in canonical order (host arrays of numAmpsPerChunk)
 void readChunk(QuregImpl& q, real* re, real* im);
 void writeChunk(QuregImpl& q, const real* re, const real* im);
@@ -105,6 +111,7 @@ struct Stats {
     long long overlappedSwaps = 0;   // swaps issued on their own stream (be::swapOverlapBegin)
     long long overlappedPasses = 0;  // passes started on the part a swap in flight leaves in place
     long long placementProbes = 0;   // re / im placements measured by the allocation probe
+    long long pauliPasses = 0, pauliTerms = 0;  // passes made for Pauli expectation values / strings evaluated
 };
 Stats& stats();
 

@@ -843,6 +843,50 @@ double densDiagSum(QuregImpl& q, const u64* offs, int n, int skipBit, i64 chunkS
     return s;
 }
 
+void pauliExpec(QuregImpl& q, int nTerms, const u64* x, const u64* z, double* out) {
+    flush(q);
+    for (int t = 0; t < nTerms; t++) {
+        const i64 xt = (i64)x[t];
+        const u64 zt = z[t];
+        const bool odd = __builtin_popcountll(x[t] & z[t]) & 1;
+        double s = 0;
+#pragma omp parallel for reduction(+ : s) if (q.numAmpsPerChunk >= kOmpMin)
+        for (i64 i = 0; i < q.numAmpsPerChunk; i++) {
+            const i64 j = i ^ xt;
+            // conj(a_j) a_i: its real part, or its imaginary part for an odd number of Y's
+            const double v = odd ? (double)q.re[j] * q.im[i] - (double)q.im[j] * q.re[i]
+                                 : (double)q.re[j] * q.re[i] + (double)q.im[j] * q.im[i];
+            s += (__builtin_popcountll((u64)i & zt) & 1) ? -v : v;
+        }
+        out[2 * t] = odd ? 0 : s;
+        out[2 * t + 1] = odd ? s : 0;
+    }
+}
+
+void densPauliExpec(QuregImpl& q, const u64* rowOffs, const u64* colOffs, int n, i64 chunkStart, int nTerms,
+                    const u64* x, const u64* z, double* out) {
+    flush(q);
+    const i64 dim = (i64)1 << n;
+    for (int t = 0; t < nTerms; t++) {
+        double sr = 0, si = 0;
+        for (i64 r = 0; r < dim; r++) {
+            const i64 c = r ^ (i64)x[t];
+            i64 p = 0;
+            for (int j = 0; j < n; j++) {
+                if ((r >> j) & 1) p |= (i64)rowOffs[j];
+                if ((c >> j) & 1) p |= (i64)colOffs[j];
+            }
+            p -= chunkStart;
+            if (p < 0 || p >= q.numAmpsPerChunk) continue;
+            const bool neg = __builtin_popcountll((u64)r & z[t]) & 1;
+            sr += neg ? -(double)q.re[p] : (double)q.re[p];
+            si += neg ? -(double)q.im[p] : (double)q.im[p];
+        }
+        out[2 * t] = sr;
+        out[2 * t + 1] = si;
+    }
+}
+
 void axpby(QuregImpl& a, real alpha, QuregImpl& b, real beta) {
     flush(a);
     flush(b);

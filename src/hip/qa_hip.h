@@ -240,6 +240,11 @@ void reduceInnerPerm(const real* ar, const real* ai, const real* br, const real*
                      double out[2]);
 double reduceMaxDiff(const real* ar, const real* ai, const real* br, const real* bi, i64 n);
 double reduceDensDiag(const real* re, i64 chunkAmps, const u64* offs, int nq, int skipBit, i64 chunkStart);
+// Pauli strings (kernels_pauli.hip; be::pauliExpec / be::densPauliExpec): nTerms <= QUEST_PAULI_MAX_TERMS_PER_PASS,
+// out[2t], out[2t+1] = Re, Im of term t's sum over the chunk
+void reducePauli(const real* re, const real* im, int L, int nTerms, const u64* x, const u64* z, double* out);
+void reduceDensPauli(const real* re, const real* im, i64 chunkAmps, const u64* rowOffs, const u64* colOffs, int nq,
+                     i64 chunkStart, int nTerms, const u64* x, const u64* z, double* out);
 double reduceDensFidelity(const real* re, const real* im, i64 n, const real* pr, const real* pi, int nq,
                           i64 chunkStart);
 
